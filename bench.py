@@ -25,6 +25,20 @@ cfg5 (10^8 x 16 with harness-injected faults: 1% churn, 1% push-batch drop, 1%
 pull-batch drop per node per round, Philox stream 3).  The default line is
 cfg4, the configuration the metric is quoted on that fits one GPU.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the
+headline needs: it builds the network, runs W warmup rounds, times K rounds
+and prints the line; roofline.achieved comes from the HIP events of those K
+rounds and roofline.traffic from the committed profile.  --full adds every leg
+that takes a run of its own: the live PMC passes (--pmc auto), cpu_baseline,
+cpu_best and the untimed spread run (--no-cpu-baseline, --no-spread and --pmc
+off switch single legs of a --full run off).
+
+--dump-outputs DIR writes, after the timed rounds and before anything else
+touches the network, what a caller of the timed path holds after its last
+round (DIR/<name>.npy, float32 / float64; dump_outputs below).  The workload is
+a pure function of the arguments (Philox streams keyed by --seed), so two
+builds run with the same arguments can be compared output for output.
+
 Multi-GPU (python -m torch.distributed.run ... bench.py --gpus N, or plain
 `python bench.py --gpus N`, which starts that launcher itself): ONE network
 of the same n x R over the N ranks, measured in both multi-GPU modes one after
@@ -66,7 +80,7 @@ CONFIGS = {
 }
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
@@ -80,10 +94,16 @@ def parse():
     p.add_argument("--schedule", default="2P", choices=["2P", "SEQ"],
                    help="2P (default) or SEQ (the reference harness's literal order; N>1: rumor slices)")
     p.add_argument("--seed", type=lambda s: int(s, 0), default=0x5AFE6055)
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg that takes a run of its own: live PMC traffic (--pmc auto), "
+                        "cpu_baseline, cpu_best and the rounds-to-full-spread run")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed rounds, write what the last of them left (DIR/<name>.npy)")
     p.add_argument("--cpu-seconds", type=float, default=15.0,
                    help="budget of the CPU-oracle sample")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-spread", action="store_true", help="skip the rounds-to-full-spread run")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
+    p.add_argument("--no-spread", action="store_true",
+                   help="with --full: skip the rounds-to-full-spread run")
     p.add_argument("--parts", type=int, default=None,
                    help="pipeline parts per rank (N>1; default 4 with RCCL: the exchanges of one "
                         "part overlap the round kernel of another)")
@@ -98,13 +118,16 @@ def parse():
                    help="run a multi-GPU mode even at N=1 (one RCCL rank: node-shard exchanges are "
                         "self-copies, the slice all-reduce a no-op; measures that path's overhead)")
     p.add_argument("--pmc", default="auto", choices=["auto", "off"],
-                   help="auto (N=1, single engine): measure roofline.traffic live -- two child "
+                   help="auto (with --full, N=1, single engine): measure roofline.traffic live -- two child "
                         "rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of this same workload and "
                         "library; off: take it from the committed profiles/pmc_n*_r*.json")
     p.add_argument("--dist-backend", default="nccl",
                    help="nccl (RCCL, one GPU per rank) or gloo (host-staged rows; rehearsal of "
                         "the N>1 path with several ranks on one GPU)")
-    a = p.parse_args()
+    a = p.parse_args(argv)
+    if not a.full:  # a plain run: the timed rounds and their line only
+        a.no_cpu_baseline = a.no_spread = True
+        a.pmc = "off"
     n, R, f = CONFIGS[a.config]
     a.nodes = n if a.nodes is None else a.nodes
     a.rumors = R if a.rumors is None else a.rumors
@@ -123,6 +146,58 @@ def inject_all(net, epoch):
             if not s.lo <= x < s.lo + s.m:
                 continue
         net.send_new(x, r)
+
+
+DUMP_SAMPLE = 1 << 18  # nodes per dumped array at most (33 MB of files at R = 256)
+DUMP_BYTES = 60 << 20   # all the dumped files together stay below this
+
+
+def dump_sample_size(n, R):
+    """Nodes dumped: per node (1 + 5) f64 and (1 + 4 ceil(R/64) + 4) f32."""
+    per_node = 8 * 6 + 4 * (5 + 4 * ((R + 63) // 64))
+    return min(n, DUMP_SAMPLE, DUMP_BYTES // per_node)
+
+
+def dump_outputs(net, mode, out_dir, seed):
+    """--dump-outputs: what the network holds after the last timed round, as a
+    caller's observers return it, in .npy files of float32 / float64 (every
+    value below is an integer those types hold exactly).
+
+    Always: known_counts (known node-rumor pairs, nodes knowing every rumor).
+    Single engine also, over a fixed sample of nodes (all of them if
+    dump_sample_size allows; else that many distinct ids drawn by numpy's
+    default_rng seeded with --seed, ascending): sample_nodes, statistics (gs_statistics_all
+    rows), known_popcounts, known_words and state_digest (gs_known_all's and
+    gs_state_digest's u64 words as four 16-bit limbs each, low first; the
+    digest covers every state code, record summary and Statistics counter).
+    Multi-GPU modes prefix the file names with the mode; every rank calls the
+    collective observer, rank 0 writes."""
+    import numpy as np
+    pre = "" if mode == "single" else mode + "_"
+    rank0 = int(os.environ.get("RANK", "0")) == 0
+
+    def put(name, arr, dt):
+        if rank0:
+            os.makedirs(out_dir, exist_ok=True)
+            np.save(os.path.join(out_dir, pre + name + ".npy"), np.ascontiguousarray(arr, dtype=dt))
+
+    def limbs(words):  # (S, w) u64 -> (S, 4w) f32 of 16-bit limbs
+        w = np.ascontiguousarray(words, dtype=np.uint64).reshape(len(words), -1)
+        return w.view(np.uint16).astype(np.float32)
+
+    put("known_counts", np.array(net.known_counts(), dtype=np.uint64), np.float64)
+    if mode != "single":
+        return
+    n, S = net.n, dump_sample_size(net.n, net.R)
+    if S == n:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=S, replace=False))
+    put("sample_nodes", idx, np.float64)
+    put("statistics", net.statistics_all()[idx], np.float64)
+    put("known_popcounts", net.known_popcounts()[idx], np.float32)
+    put("known_words", limbs(net.known_all()[idx]), np.float32)
+    put("state_digest", limbs(net.state_digest()[idx]), np.float32)
 
 
 def spread_run(net, epoch, max_rounds=200):
@@ -345,6 +420,8 @@ def run_mode(args, mode, world, rank, local, dist, sg, np, torch, with_spread):
     # counted by the kernels
     out["bytes_per"], out["launches"] = (net.round_traffic() if hasattr(net, "round_traffic")
                                          else (out["bytes_dense"], 0))
+    if args.dump_outputs:
+        dump_outputs(net, mode, args.dump_outputs, args.seed)
     out["spread"] = spread_run(net, epoch) if with_spread else None
     net.close()
     return out

@@ -9,5 +9,5 @@ R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp && cd $R
 timeout -k 10 200 python3 exp/shard_prof.py 8 30 1 > $O/shard8_wall.txt 2>&1
 AMD_SERIALIZE_KERNEL=3 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/$O/shard8 -o run -- python3 exp/shard_prof.py 8 30 1 > $O/shard8_ser.txt 2>&1
-timeout -k 10 200 python3 bench.py --rumors 32 --steps 30 --warmup 3 --no-cpu-baseline --no-spread > $O/slice32.json 2>$O/slice32.err
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/$O/slice32 -o run -- python3 bench.py --rumors 32 --steps 30 --warmup 3 --no-cpu-baseline --no-spread > /dev/null 2>>$O/slice32.err
+timeout -k 10 200 python3 bench.py --full --rumors 32 --steps 30 --warmup 3 --no-cpu-baseline --no-spread > $O/slice32.json 2>$O/slice32.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/$O/slice32 -o run -- python3 bench.py --full --rumors 32 --steps 30 --warmup 3 --no-cpu-baseline --no-spread > /dev/null 2>>$O/slice32.err

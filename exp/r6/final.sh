@@ -10,8 +10,8 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --durations=25 --timeou
 tail -n 2 $O/gpu_tests.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 500 python bench.py > $O/bench_cfg4.json 2> $O/bench.err
-timeout -k 10 300 python bench.py --config cfg5 --no-cpu-baseline > $O/bench_cfg5.json 2>> $O/bench.err
-for c in cfg2 cfg3; do timeout -k 10 200 python bench.py --config $c --no-cpu-baseline --pmc off > $O/bench_$c.json 2>> $O/bench.err; done
+timeout -k 10 500 python bench.py --full > $O/bench_cfg4.json 2> $O/bench.err
+timeout -k 10 300 python bench.py --full --config cfg5 --no-cpu-baseline > $O/bench_cfg5.json 2>> $O/bench.err
+for c in cfg2 cfg3; do timeout -k 10 200 python bench.py --full --config $c --no-cpu-baseline --pmc off > $O/bench_$c.json 2>> $O/bench.err; done
 bash profiles/rocprof_r2.sh ${T}_cfg4
 bash profiles/rocprof_r2.sh ${T}_cfg5 --config cfg5

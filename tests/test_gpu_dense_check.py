@@ -28,7 +28,7 @@ def _first_bad(a, b):
 
 # rounds to termination and first round of full spread at seed 0x5AFE6055,
 # epoch 1, every rumor injected in round 1 at its Philox origin: the spread
-# record bench.py prints for configs 3 and 4 (it times and spreads epoch 1)
+# record bench.py --full prints for configs 3 and 4 (it times and spreads epoch 1)
 SPREAD = {(1 << 20, 64): (22, 16), (1 << 24, 256): (34, 18)}
 
 
@@ -138,7 +138,7 @@ def test_config5_faults_rounds(engine):
         single.close()
 
 
-# config 5's spread record at the bench's epoch (bench.py prints it): 42
+# config 5's spread record at the bench's epoch (bench.py --full prints it): 42
 # rounds, churn keeps two nodes from some rumor, never a full spread
 SPREAD5 = (42, 0, 99_999_998)
 
