@@ -57,7 +57,10 @@ typedef enum {
     GS_ERR_HIP = -3,
     GS_ERR_OUT_OF_MEMORY = -4,
     GS_ERR_DEVICE_LIMIT = -5      /* a node's in-degree exceeded the packed
-                                     counter range (probability ~1e-34/node) */
+                                     counter range (probability ~1e-34/node);
+                                     from gs_handle_received[_batch]: a bound
+                                     on external RPCs per round, nothing of
+                                     the call applied */
 } gs_status;
 
 /* Delivery order of a round.  2P: the reference harness
@@ -420,6 +423,16 @@ gs_status   gs_push_batch(gs_engine *e, uint32_t node, uint8_t *out, uint32_t ca
  * min(200, 32 * R_pad) first Pushes per node and round
  * (GS_ERR_DEVICE_LIMIT past that: its empty answers ride the one-byte
  * per-round empty count the slices reduce with MIN).
+ * Every engine: at most 96 recorded copies of one rumor at one node in one
+ * round, that is 96 distinct peers whose last RPC for it this round carries
+ * that message (a peer's repeated copy replaces its earlier one and does not
+ * count again).  The round kernels that apply external RPCs count votes in 7
+ * bits: 96 external copies and the 31 internal ones a round can record.  The
+ * 97th is GS_ERR_DEVICE_LIMIT, and like every GS_ERR_DEVICE_LIMIT of the
+ * wire calls it applies NOTHING of the call: no peer counted, no copy
+ * queued, no Statistics change, no answer.  A network of several engines
+ * checks a batch against this bound before any engine takes a part of it
+ * (safe_gossip_amd ExtCopies).  |peers_in_this_round| itself is not bounded.
  * Messages whose bytes are no rumor slot's key: GS_ERR_INVALID_ARGUMENT.
  * A node offline this round (churn) drops the RPC: GS_OK, no frames, no
  * effect.  Undecodable bytes: GS_ERR_SERIALISATION, nothing applied; so is a
@@ -432,9 +445,11 @@ gs_status   gs_handle_received(gs_engine *e, uint32_t node, uint32_t peer, const
  * peers[i] >= n to nodes[i]), with ONE observation launch for every node a
  * first Push makes answer (instead of one per call): the responses of RPC i
  * are out[resp_off[i] .. resp_off[i+1]) (frames "u32 LE length + RPC";
- * resp_off holds count+1 offsets).  All or nothing: a malformed message, an unknown rumor or an
+ * resp_off holds count+1 offsets).  All or nothing: a malformed message, an unknown rumor, an
  * `out` smaller than the responses (GS_ERR_SERIALISATION, *out_len = bytes
- * needed) applies none of them. */
+ * needed) or an RPC past a bound of gs_handle_received (GS_ERR_DEVICE_LIMIT:
+ * a slice's first Pushes, the 96 recorded copies per node and rumor, the
+ * batch's earlier RPCs counted) applies none of them. */
 gs_status   gs_handle_received_batch(gs_engine *e, uint32_t count, const uint32_t *nodes, const uint32_t *peers,
                                      const uint8_t *msgs, const uint32_t *off, const uint32_t *len, uint8_t *out,
                                      uint32_t cap, uint32_t *out_len, uint32_t *resp_off);

@@ -461,6 +461,46 @@ def engine_push_batch(lib, h, node: int) -> List[bytes]:
     return split_frames(bytes(out)[:n.value])
 
 
+EXT_COPIES_MAX = 96  # gs_common.h kExtCopiesMax
+
+
+class ExtCopies:
+    """The engine's bound on recorded external copies -- at most
+    EXT_COPIES_MAX distinct peers outside the network may send one rumor to
+    one node in a round (``GS_ERR_DEVICE_LIMIT``, status -5) -- kept for a
+    network of several engines, where the engine that owns the rumor or the
+    node is not the only one a batch touches: the whole batch is checked
+    before any engine takes a part of it.  Every rank sees every RPC, so all
+    ranks refuse alike.  (An RPC to a node that churn has taken offline this
+    round counts here although the engine drops it: refused sooner, never
+    later, than a single engine would.)"""
+
+    def __init__(self):
+        self._peers = {}
+
+    def reset(self) -> None:
+        self._peers.clear()
+
+    def check(self, copies):
+        """``copies``: (node, rumor id, peer) of the batch's non-empty RPCs,
+        in order.  Raises DeviceError past the bound; returns what
+        ``commit`` records once the engines have applied the batch."""
+        add = {}
+        for node, rumor, peer in copies:
+            have = self._peers.get((node, rumor), ())
+            new = add.setdefault((node, rumor), set())
+            if peer in have or peer in new:
+                continue  # replaces that peer's earlier copy
+            new.add(peer)
+            if len(have) + len(new) > EXT_COPIES_MAX:
+                _check(-5)
+        return add
+
+    def commit(self, add) -> None:
+        for k, v in add.items():
+            self._peers.setdefault(k, set()).update(v)
+
+
 def engine_handle_received(lib, h, node: int, peer: int, message: bytes) -> List[bytes]:
     """gs_handle_received of one engine, the response buffer grown as needed."""
     cap = 4096

@@ -151,7 +151,10 @@ struct Geometry {
 //               ascending index order (the order Gossip::receive sees them);
 //               pushers i >= kInline are at src[first + i - kInline] (tails of
 //               the 1.9% of nodes with in-degree > 3).  k <= kMaxIn: a larger
-//               in-degree (probability ~1e-34 per node) is a device limit.
+//               in-degree (probability ~1e-34 per node) is a device limit;
+//               kMaxIn + 1 = 31 recorded copies per entry (the pushers' and
+//               one pull copy) is what the 5-bit vote counters of the round
+//               kernels without external RPCs rely on (gs_recv.h).
 //   SibRec[x] = {serial << 8 | rank, e0, e1, e2} (16 B): x's rank among the
 //               pushers of t(x) and the first kSibInline pushers ahead of it
 //               (the rest are InRec[t(x)].s / its tail); valid iff the serial
@@ -162,6 +165,13 @@ constexpr uint32_t kInline = 3;
 constexpr uint32_t kSibInline = 3;
 constexpr uint32_t kSerialMask = 0xFFFFFFu;
 constexpr uint32_t kMaxIn = 30;      // in-degree limit (5-bit k field)
+// External RPCs (gs_handle_received[_batch]): at most this many recorded
+// copies per (node, rumor) and round; one more is GS_ERR_DEVICE_LIMIT.  With
+// the kMaxIn + 1 internal copies the count stays below 2^7 (gs_recv.h).
+constexpr uint32_t kExtCopiesMax = 96;
+// widths of the round kernels' bit-sliced vote counters: without / with
+// external RPCs applied (gs_recv.h)
+constexpr int kVoteBits = 5, kVoteBitsExt = 7;
 constexpr uint32_t kFirstShift = 5;  // tails: first < 2^27
 struct alignas(16) InRec {
     uint32_t kf, s[kInline];
@@ -238,7 +248,10 @@ __host__ __device__ inline u64 digest_plane_k(uint32_t p) { return 0x9E3779B97F4
 // post-delivery bit-sliced state: entries in A/B/C/D before the deliveries
 // (B, C, D; a0, a1 and the five b planes bp), the entries the deliveries
 // created (crB: B{0,1}, crC: C{0,0}), and the record counters of B entries
-// (anyC; c1: #counters in [1, counter_max); c2: #counters == 2).
+// (anyC; c1: #counters in [1, counter_max); c2: #counters == 2).  Only the
+// low five bits of c1 and c2 enter the digest, whatever the caller's counter
+// width: the dense checks the digest serves carry no external RPCs, so their
+// counts stay below 32, and gs_dump_records reports the full 7-bit counts.
 __host__ __device__ inline void digest_planes(u64 m, u64 B, u64 C, u64 D, u64 crB, u64 crC, u64 a0, u64 a1,
                                               const u64 *bp, u64 anyC, const u64 *c1, const u64 *c2, u64 pl[20]) {
     const u64 BC = B | C, E = B | crB;

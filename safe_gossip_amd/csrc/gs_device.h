@@ -62,10 +62,12 @@ GS_DEV uint32_t popcT(T v) {
     if constexpr (sizeof(T) == 8) return (uint32_t)__popcll(v);
     else return (uint32_t)__popc(v);
 }
-template <typename T>
-GS_DEV void add5T(T (&c)[5], T in) {
+// c += in for bit-sliced NB-bit counters (5: internal deliveries only; 7: the kernels
+// that also apply external RPCs, gs_recv.h kVoteBitsExt); wraps modulo 2^NB
+template <int NB, typename T>
+GS_DEV void addcT(T (&c)[NB], T in) {
 #pragma unroll
-    for (int i = 0; i < 5; ++i) {
+    for (int i = 0; i < NB; ++i) {
         const T t = c[i] & in;
         c[i] ^= in;
         in = t;

@@ -48,7 +48,7 @@ static_assert(GS_DLV4_TAIL_PRE <= 3, "tail prefetch depth");
 
 // The lane word T holds the lane's nodes side by side (u32: two 16-bit or
 // four <= 8-bit segments; u64: four 16-bit segments); the bit-sliced helpers
-// of gs_device.h (popcT, add5T, ge_uT) take either width.
+// of gs_device.h (popcT, addcT, ge_uT) take either width.
 // "x >= K" with K given per segment: km[i] holds bit i of every segment's K
 // spread over that segment.
 template <int NB, typename T>
@@ -67,6 +67,8 @@ GS_DEV T ge_seg(const T (&x)[NB], const T (&km)[NB]) {
 // EXT: the round's external RPCs (gs_handle_received) are applied after the
 // internal deliveries, as in round_kernel (gs_kernels.hip, the a.n_ext
 // block); a variant of its own, launched only for a round that has some.
+// Its vote counters and thresholds are kVoteBitsExt = 7 bits wide (gs_recv.h:
+// external copies are not bounded by the in-degree), the others' 5.
 template <int MODE, typename T, uint32_t kNpl, bool SH = false, bool EXT = false>
 __global__ __launch_bounds__(kDlv4Threads, (kNpl == 2 && sizeof(T) == 4) ? GS_DLV4_MINW_R16 : GS_DLV4_MINW)
 void round_kernel_dlv4(RoundArgs a) {
@@ -209,7 +211,10 @@ void round_kernel_dlv4(RoundArgs a) {
 
     // ---- phases 1 and 2 of round t (Gossip::receive), four nodes at once
     T notyet = A, recB = B, oc1r = B & a0 & ~a1, crB = 0, crC = 0, anyC = 0;
-    T cv[5] = {0, 0, 0, 0, 0};
+    constexpr int kNB = EXT ? kVoteBitsExt : kVoteBits;
+    T cv[kNB];
+#pragma unroll
+    for (int i = 0; i < kNB; ++i) cv[i] = 0;
     uint32_t part_cw[kNpl], fc[kNpl], recv[kNpl], psize[kNpl];
     T pulledM = 0, offM = 0;
 #pragma unroll
@@ -250,7 +255,7 @@ void round_kernel_dlv4(RoundArgs a) {
             const T newc = notyet & sl;           // new_from_peer: not recorded
             const T rec = recB & sl & recm;       // MessageState::receive on B
             anyC |= rec & vC;
-            add5T(cv, rec & vB & (v2 | oc1r));
+            addcT(cv, rec & vB & (v2 | oc1r));
             crB |= newc & ~vC;
             crC |= newc & vC;
             recB |= newc & ~vC;
@@ -280,7 +285,7 @@ void round_kernel_dlv4(RoundArgs a) {
             const T newc = notyet & pl;
             const T rec = recB & pl;
             anyC |= rec & pCl;
-            add5T(cv, rec & pvB & (pv2 | oc1r));
+            addcT(cv, rec & pvB & (pv2 | oc1r));
             crB |= newc & ~pCl;
             crC |= newc & pCl;
             recB |= newc & ~pCl;
@@ -331,7 +336,7 @@ void round_kernel_dlv4(RoundArgs a) {
                 const T newc = notyet & bit;
                 const T rec = recB & bit & ((info & kExtRec) ? (T)~(T)0 : (T)0);
                 anyC |= rec & vC;
-                add5T(cv, rec & vB & (v2 | oc1r));
+                addcT(cv, rec & vB & (v2 | oc1r));
                 crB |= newc & ~vC;
                 crC |= newc & vC;
                 recB |= newc & ~vC;
@@ -380,16 +385,18 @@ void round_kernel_dlv4(RoundArgs a) {
     const T oc1 = (Bold & a0 & ~a1) | cB | inj;
     const T oc2 = Bold & a1 & ~a0;
     // median rule with 0-filled peers: bump iff ge >= |P|/2 + 1, per node
-    T km[5] = {0, 0, 0, 0, 0}, kbig = 0;
+    T km[kNB], kbig = 0;
+#pragma unroll
+    for (int i = 0; i < kNB; ++i) km[i] = 0;
 #pragma unroll
     for (uint32_t q = 0; q < kNpl; ++q) {
         const uint32_t thr = psize[q] / 2u + 1u;
 #pragma unroll
-        for (int i = 0; i < 5; ++i)
+        for (int i = 0; i < kNB; ++i)
             if ((thr >> i) & 1u) km[i] |= M[q];
-        if (thr >= 32u) kbig |= M[q];
+        if (thr >= (1u << kNB)) kbig |= M[q];  // above every count the counters hold: never
     }
-    T bump = ge_seg<5>(cv, km) & ~kbig & (Bold | cB);
+    T bump = ge_seg<kNB>(cv, km) & ~kbig & (Bold | cB);
     T anyCe = anyC & ninj;
     if (DELIVER && offM) {  // back from offline: the votes its skipped next_round kept
 #pragma unroll

@@ -14,6 +14,7 @@
 #include <map>
 #include <set>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -128,6 +129,11 @@ struct gs_engine {
     std::vector<Ext> ext;                   // in call order
     std::set<std::pair<uint32_t, uint32_t>> ext_peers;  // (node, peer) heard from this round
     std::map<uint32_t, uint32_t> ext_fp;  // rumor slices: answered external first Pushes per node this round
+    // recorded external copies this round (the queue's kExtRec entries): the
+    // (node, rumor, peer) that have one, and their number per (node, rumor),
+    // at most gs::kExtCopiesMax (the EXT round kernels' 7-bit vote counters)
+    std::set<std::tuple<uint32_t, uint32_t, uint32_t>> ext_copy_peers;
+    std::map<std::pair<uint32_t, uint32_t>, uint32_t> ext_copies;
     uint32_t ext_limit = 0;               // rumor slices: the network's bound on them (0: this slice's own)
     u64 *ext_dev = nullptr;
     uint32_t ext_cap = 0, ext_uploaded = 0;
@@ -264,6 +270,8 @@ gs_status reset_state(gs_engine *e) {
     e->ext.clear();
     e->ext_peers.clear();
     e->ext_fp.clear();
+    e->ext_copy_peers.clear();
+    e->ext_copies.clear();
     e->ext_uploaded = 0;
     return GS_OK;
 }
@@ -574,7 +582,7 @@ const char *gs_status_string(gs_status s) {
     case GS_ERR_UNSUPPORTED: return "parameters outside the packed state layout (counter_max<=3, max_c_rounds<=3, max_rounds<=32, R<=4096), or a shard layout the engine cannot hold (class-row rank above 33.3 M nodes)";
     case GS_ERR_HIP: return "HIP runtime error (no usable MI355X device?)";
     case GS_ERR_OUT_OF_MEMORY: return "out of device memory";
-    case GS_ERR_DEVICE_LIMIT: return "device limit hit (in-degree > 30, in-list or receive-row capacity, SEQ depth)";
+    case GS_ERR_DEVICE_LIMIT: return "device limit hit (in-degree > 30, in-list or receive-row capacity, SEQ depth, more than 96 recorded external copies of a rumor at a node in one round, a rumor slice's external first Pushes per node and round)";
     }
     return "unknown";
 }
@@ -1250,6 +1258,8 @@ gs_status round_end(gs_engine *e, gs_round_report *report) {
     e->ext.clear();  // delivered by this round kernel (upload_ext syncs before reuse)
     e->ext_peers.clear();
     e->ext_fp.clear();
+    e->ext_copy_peers.clear();
+    e->ext_copies.clear();
     e->ext_uploaded = 0;
     e->obs_valid = false;
     if (++e->since_fold >= e->fold_every) {
@@ -1786,6 +1796,10 @@ gs_status gs_handle_received_batch(gs_engine *e, uint32_t count, const uint32_t 
     std::vector<Item> it(count);
     std::set<std::pair<uint32_t, uint32_t>> peers_seen(e->ext_peers);
     std::map<uint32_t, uint32_t> fp;  // slices: first Pushes per node, this batch included
+    // recorded copies per (node, rumor), this batch included (gs::kExtCopiesMax):
+    // a peer's later copy of the same rumor replaces its earlier one
+    std::set<std::tuple<uint32_t, uint32_t, uint32_t>> new_copies;
+    std::map<std::pair<uint32_t, uint32_t>, uint32_t> copies;
     std::vector<uint32_t> obs;
     for (uint32_t i = 0; i < count; ++i) {
         Item &v = it[i];
@@ -1807,6 +1821,15 @@ gs_status gs_handle_received_batch(gs_engine *e, uint32_t count, const uint32_t 
         // churn: a node the harness took offline this round drops it
         v.offline = e->faults.churn && gs::offline_of(e->seed, e->epoch, e->round, nodes[i], e->faults.churn);
         v.is_new = !v.offline && peers_seen.insert({v.node, v.peer}).second;  // src/gossip.rs:125
+        if (!v.offline && !v.empty && !e->ext_copy_peers.count({v.node, v.rumor, v.peer}) &&
+            new_copies.insert({v.node, v.rumor, v.peer}).second) {
+            auto c = copies.find({v.node, v.rumor});
+            if (c == copies.end()) {
+                auto h = e->ext_copies.find({v.node, v.rumor});
+                c = copies.emplace(std::make_pair(v.node, v.rumor), h == e->ext_copies.end() ? 0u : h->second).first;
+            }
+            if (++c->second > gs::kExtCopiesMax) return GS_ERR_DEVICE_LIMIT;
+        }
         if (v.is_new && !v.pull) {
             obs.push_back(v.node);
             if (e->slice) {  // (see slice_ext_limit)
@@ -1889,6 +1912,8 @@ gs_status gs_handle_received_batch(gs_engine *e, uint32_t count, const uint32_t 
     frames(true);
     // queue every RPC as gs_handle_received does, in call order
     for (auto &f : fp) e->ext_fp[f.first] = f.second;
+    for (auto &c : copies) e->ext_copies[c.first] = c.second;
+    e->ext_copy_peers.insert(new_copies.begin(), new_copies.end());
     for (uint32_t i = 0; i < count; ++i) {
         const Item &v = it[i];
         if (v.offline) continue;
@@ -1995,6 +2020,13 @@ gs_status gs_handle_received(gs_engine *e, uint32_t node, uint32_t peer, const u
     if (st != GS_OK) return st;
     const bool fresh = !e->ext_peers.count({node, peer});  // src/gossip.rs:125
     if (fresh && !pull && e->slice && e->ext_fp[node] >= slice_ext_limit(e)) return GS_ERR_DEVICE_LIMIT;
+    // one more recorded copy of this rumor at this node than the round kernel's
+    // counters hold (a peer's repeated copy replaces its earlier one)
+    const bool new_copy = !empty && !e->ext_copy_peers.count({node, rumor, peer});
+    if (new_copy) {
+        auto c = e->ext_copies.find({node, rumor});
+        if (c != e->ext_copies.end() && c->second >= gs::kExtCopiesMax) return GS_ERR_DEVICE_LIMIT;
+    }
     const bool is_new = e->ext_peers.insert({node, peer}).second;
     if (is_new && !pull) {
         // Pull responses: the node's live entries now (src/gossip.rs:126-148)
@@ -2032,6 +2064,10 @@ gs_status gs_handle_received(gs_engine *e, uint32_t node, uint32_t peer, const u
         for (auto &x : e->ext)
             if (x.node == node && x.peer == peer && !(x.info & gs::kExtEmpty) && (x.info & 0xFFFu) == rumor)
                 x.info &= ~gs::kExtRec;
+    }
+    if (new_copy) {
+        e->ext_copy_peers.insert({node, rumor, peer});
+        ++e->ext_copies[{node, rumor}];
     }
     e->ext.push_back({node, (uint32_t)e->ext.size(), info, peer});
     e->ext_uploaded = (uint32_t)-1;  // re-upload

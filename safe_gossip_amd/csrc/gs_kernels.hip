@@ -70,6 +70,10 @@ static_assert(kRkSmallBlk == 64u || kRkSmallBlk == 128u, "a thread's stage step 
 // by the level passes, and it is absorbed at x's own position among its
 // pushers (time x), answered pushes included.
 // DLV (R_pad <= 16, 2P): a push code (b0 | b1 << 16) as class planes.
+// EXT: the launch applies external RPCs (a.n_ext != 0; delivering modes
+// only): its vote counters are kVoteBitsExt bits wide instead of kVoteBits
+// (gs_recv.h).  launch_mode picks it for exactly those launches, so the
+// kernels of a round without external RPCs are the 5-bit ones.
 GS_DEV Cls decode16(uint32_t code) {
     const u64 b0 = code & 0xFFFFu, b1 = code >> 16;
     return Cls{b0 & b1, b0 & ~b1, b1 & ~b0};
@@ -78,9 +82,10 @@ GS_DEV Cls decode16(uint32_t code) {
 // DLV: delivery records (gs_common.h DlvRec) replace every class-plane
 // gather: a lane's pushers' push codes are in its own record and its pull
 // batch in PULL[x], both read coalesced.
-template <bool SMALL, int MODE, bool SHARD, bool SEQ, bool DLV, uint32_t BLK = 256u>
+template <bool SMALL, int MODE, bool SHARD, bool SEQ, bool DLV, uint32_t BLK = 256u, bool EXT = false>
 __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) void round_kernel(RoundArgs a) {
     constexpr bool DELIVER = (MODE == 1 || MODE == 2);
+    static_assert(!EXT || DELIVER, "external RPCs are applied with the round's deliveries");
     constexpr bool TRANSITION = (MODE == 0 || MODE == 1);
     const Geometry &g = a.g;
     // words of planes one block owns (its records are contiguous), uint4
@@ -329,7 +334,8 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
     // own push copy, if any, stays recorded.
     const bool off_t = DELIVER && (tgw & kTgOff);
     const bool pulled = !(tgw & kTgNoPull);
-    Recv<!TRANSITION> rv;
+    using RecvT = Recv<!TRANSITION, u64, EXT ? kVoteBitsExt : kVoteBits>;
+    RecvT rv;
     rv.init(A, B, B & a0 & ~a1);
     uint32_t psize = 0;
     uint32_t ext_new = 0, ext_full = 0, ext_empty = 0, ext_recv = 0;  // external RPCs (node level)
@@ -519,7 +525,9 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
             rv.create(newc, pCl);
         }
         rv.recv += popc(pl);
-        if (a.n_ext) {
+        if (a.n_ext) {  // (a runtime test in every instantiation, as before EXT existed: the
+                        // 5-bit kernels compile to the code they had; launch_mode gives
+                        // them no launch with a queue)
             // External RPCs to x (gs_handle_received), after every internal
             // delivery of the round, in call order (Gossip::receive,
             // src/gossip.rs:118-163): a first RPC from a peer joins
@@ -699,7 +707,7 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
                     if ((B | crB) & bit) {
                         uint32_t v1 = 0, v2 = 0;
 #pragma unroll
-                        for (int i = 0; i < 5; ++i) {
+                        for (int i = 0; i < RecvT::kNB; ++i) {  // (7 bits each in the record format)
                             v1 |= (uint32_t)((rv.c1[i] >> b) & 1u) << i;
                             v2 |= (uint32_t)((rv.c2[i] >> b) & 1u) << i;
                         }
@@ -887,6 +895,7 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
 
 template <bool SMALL, bool SHARD, bool SEQ, bool DLV = false>
 static hipError_t launch_mode(const RoundArgs &a, int mode, hipStream_t s) {
+    const bool ext = a.n_ext > 0 && (mode == 1 || mode == 2);  // the EXT instantiations
     if constexpr (!SMALL && !SEQ && !DLV) {
         if ((mode == 0 || mode == 1) && a.g.W <= 16u) {
             if (a.blk_list) return hipErrorInvalidValue;  // (observation launches only)
@@ -903,6 +912,9 @@ static hipError_t launch_mode(const RoundArgs &a, int mode, hipStream_t s) {
             if (mode == 0)
                 hipLaunchKernelGGL((round_kernel<false, 0, SHARD, false, false, kRkSmallBlk>), dim3((uint32_t)(b1 - b0)),
                                    dim3(kRkSmallBlk), 0, s, b);
+            else if (ext)
+                hipLaunchKernelGGL((round_kernel<false, 1, SHARD, false, false, kRkSmallBlk, true>),
+                                   dim3((uint32_t)(b1 - b0)), dim3(kRkSmallBlk), 0, s, b);
             else
                 hipLaunchKernelGGL((round_kernel<false, 1, SHARD, false, false, kRkSmallBlk>), dim3((uint32_t)(b1 - b0)),
                                    dim3(kRkSmallBlk), 0, s, b);
@@ -915,8 +927,14 @@ static hipError_t launch_mode(const RoundArgs &a, int mode, hipStream_t s) {
     if (a.blk_list && (mode == 0 || mode == 1)) return hipErrorInvalidValue;  // (observation launches only)
     switch (mode) {
     case 0: hipLaunchKernelGGL((round_kernel<SMALL, 0, SHARD, SEQ, DLV>), dim3((uint32_t)grid), dim3(block), 0, s, a); break;
-    case 1: hipLaunchKernelGGL((round_kernel<SMALL, 1, SHARD, SEQ, DLV>), dim3((uint32_t)grid), dim3(block), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((round_kernel<SMALL, 2, SHARD, SEQ, DLV>), dim3((uint32_t)grid), dim3(block), 0, s, a); break;
+    case 1:
+        if (ext) hipLaunchKernelGGL((round_kernel<SMALL, 1, SHARD, SEQ, DLV, 256u, true>), dim3((uint32_t)grid), dim3(block), 0, s, a);
+        else hipLaunchKernelGGL((round_kernel<SMALL, 1, SHARD, SEQ, DLV>), dim3((uint32_t)grid), dim3(block), 0, s, a);
+        break;
+    case 2:
+        if (ext) hipLaunchKernelGGL((round_kernel<SMALL, 2, SHARD, SEQ, DLV, 256u, true>), dim3((uint32_t)grid), dim3(block), 0, s, a);
+        else hipLaunchKernelGGL((round_kernel<SMALL, 2, SHARD, SEQ, DLV>), dim3((uint32_t)grid), dim3(block), 0, s, a);
+        break;
     default: hipLaunchKernelGGL((round_kernel<SMALL, 3, SHARD, SEQ, DLV>), dim3((uint32_t)grid), dim3(block), 0, s, a); break;
     }
     return hipGetLastError();

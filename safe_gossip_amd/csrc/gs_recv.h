@@ -24,16 +24,29 @@ constexpr uint32_t kBatchE = GS_BATCH_E;
 // (MessageState::next_round's greater_or_equal, src/message_state.rs:118-129);
 // the observation path (OBS) keeps the two counters the parity dumps report.
 // T is the lane word: u64 (64 rumors per lane) or u32 (gs_w32.hip).
-template <bool OBS, typename T = u64>
+//
+// NB is the counters' width.  Internal deliveries record at most kMaxIn push
+// copies and one pull copy per entry, so kVoteBits = 5 bits hold every count
+// of a round without external RPCs, and a threshold |P|/2 + 1 <= 16 is always
+// below 2^5.  External RPCs (gs_handle_received) have no in-degree cap: the
+// instantiations that apply them (EXT) count in kVoteBitsExt = 7 bits, the
+// width of the oracle's record format, and the host refuses more than
+// kExtCopiesMax recorded external copies per (node, rumor) and round, so a
+// count never wraps; a threshold >= 2^7 is then "never" exactly.
+static_assert(kMaxIn + 1u < (1u << kVoteBits), "5-bit vote counters hold kMaxIn push copies + one pull copy");
+static_assert(kMaxIn + 1u + kExtCopiesMax < (1u << kVoteBitsExt),
+              "7-bit vote counters hold the internal copies + kExtCopiesMax external ones");
+template <bool OBS, typename T = u64, int NB = kVoteBits>
 struct Recv {
+    static constexpr int kNB = NB;
     T notyet;            // still absent: the next live copy creates the entry
     T recB;              // entries in state B (existing or created): record copies
     T oc1;               // B entries whose our_counter is 1 (created ones included)
     T crB, crC;          // created this round as B{0,1} / C{0,0}
     T anyC;              // a recorded counter >= counter_max
-    T cv[5];             // #recorded counters >= our_counter (and < counter_max)
-    T c1[5];             // OBS only: #recorded counters in [1, counter_max)
-    T c2[5];             // OBS only: #recorded counters == 2 (< counter_max)
+    T cv[NB];            // #recorded counters >= our_counter (and < counter_max)
+    T c1[NB];            // OBS only: #recorded counters in [1, counter_max)
+    T c2[NB];            // OBS only: #recorded counters == 2 (< counter_max)
     uint32_t part_cw;    // sum over pushers i of (k-1-i) * |created by i|
     uint32_t first_create;
     uint32_t recv;       // copies received (push rows + pull row)
@@ -44,10 +57,10 @@ struct Recv {
         oc1 = Boc1;
         crB = crC = anyC = 0;
 #pragma unroll
-        for (int i = 0; i < 5; ++i) cv[i] = 0;
+        for (int i = 0; i < NB; ++i) cv[i] = 0;
         if constexpr (OBS) {
 #pragma unroll
-            for (int i = 0; i < 5; ++i) c1[i] = c2[i] = 0;
+            for (int i = 0; i < NB; ++i) c1[i] = c2[i] = 0;
         }
         part_cw = 0;
         first_create = kNone;
@@ -56,10 +69,10 @@ struct Recv {
     // Record copies `rec` of class (vB: a B counter, v2: counter 2, vC: 255).
     GS_DEV void record(T rec, T vB, T v2, T vC) {
         anyC |= rec & vC;
-        add5T(cv, rec & vB & (v2 | oc1));
+        addcT(cv, rec & vB & (v2 | oc1));
         if constexpr (OBS) {
-            add5T(c1, rec & vB);
-            add5T(c2, rec & v2);
+            addcT(c1, rec & vB);
+            addcT(c2, rec & v2);
         }
     }
     GS_DEV void create(T newc, T vC) {
@@ -157,7 +170,7 @@ GS_DEV void next_round_seg(const T (&P)[kPlanes], const RV &rv, T inj, uint32_t 
         bump = pbump & Bold;
         anyCe = panyC & ninj;
     } else {
-        bump = ge_kT<5>(rv.cv, psize / 2u + 1u) & (Bold | cB);  // cv counts only B entries' votes
+        bump = ge_kT<RV::kNB>(rv.cv, psize / 2u + 1u) & (Bold | cB);  // cv counts only B entries' votes
         anyCe = rv.anyC & ninj;
     }
     T nr[6];  // round + 1

@@ -39,7 +39,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import (DeviceError, GossipError, NoPeers, RoundReport, _buf, _check, _Config, _Report,
+from . import (DeviceError, ExtCopies, GossipError, NoPeers, RoundReport, _buf, _check, _Config, _Report,
                engine_handle_received_batch, engine_push_batch, fault_threshold, load_library, rpc_decode)
 
 # RCCL's all_to_all_single is exact up to 2^30 bytes per rank (DESIGN.md
@@ -183,6 +183,7 @@ class ShardedNetwork:
         # than asked: gs_shard_info reports the effective count)
         self.parts = self.shards[0].parts
         self.round = 0
+        self._ext_copies = ExtCopies()
         self._delivered = True
         self._pendA = []   # async works of exchange A of the current round
         self._pendB = {}   # part -> async work of exchange B of the current round
@@ -344,6 +345,7 @@ class ShardedNetwork:
                 _check(self.lib.gs_next_round(s.h, None))
         self._pendA.append(self._exchange("A", self.parts - 1, k))
         self.round += 1
+        self._ext_copies.reset()
         self._delivered = False
         if not report:
             return None
@@ -360,6 +362,7 @@ class ShardedNetwork:
         for s in self.shards:
             _check(self.lib.gs_clear(s.h, self.epoch))
         self.round = 0
+        self._ext_copies.reset()
         self._delivered = True
 
     def sync(self) -> None:
@@ -416,12 +419,17 @@ class ShardedNetwork:
         if getattr(self, "_keys", None) is None:  # (2 FFI calls per rumor: built once per key change)
             self._keys = {self.rumor_key(r) for r in range(self.R)}
         keys = self._keys
+        copies = []
         for node, peer, msg in rpcs:
             if not 0 <= node < self.n or peer < self.n:
                 _check(-1)
             _, m, ctr = rpc_decode(msg)
             if (m or ctr) and m not in keys:
                 _check(-1)
+            if m or ctr:
+                copies.append((node, m, peer))
+        # the bound on recorded copies, across the shards a batch touches
+        return self._ext_copies.check(copies)
 
     def handle_received(self, node: int, peer: int, message: bytes) -> List[bytes]:
         """``Gossiper::handle_received_message(peer, message)`` on ``node`` for
@@ -433,7 +441,7 @@ class ShardedNetwork:
         """``handle_received`` for many (node, peer, message) in order; each
         shard takes its nodes' RPCs in one gs_handle_received_batch."""
         rpcs = list(rpcs)
-        self._validate(rpcs)
+        add = self._validate(rpcs)
         self._per_shard(lambda s: None)  # round delivered: pull rows in, exchange B waited for
         mine = {}
         for s in self.shards:
@@ -441,6 +449,7 @@ class ShardedNetwork:
             if idx:
                 for i, resp in zip(idx, engine_handle_received_batch(self.lib, s.h, [rpcs[i] for i in idx])):
                     mine[i] = resp
+        self._ext_copies.commit(add)
         out = {}
         for d in self._share(mine):
             out.update(d)

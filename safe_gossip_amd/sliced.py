@@ -39,7 +39,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import (_U64P, GossipError, Network, NoPeers, RoundReport, Statistics, _check, default_rumor_key,
+from . import (_U64P, ExtCopies, GossipError, Network, NoPeers, RoundReport, Statistics, _check, default_rumor_key,
                rpc_decode, rpc_encode)
 
 
@@ -160,6 +160,7 @@ class SlicedNetwork:
         # the slices' engines take the network's keys on first use
         self._key_of, self._rumor_of = {}, {}
         self._keys_ready = False
+        self._ext_copies = ExtCopies()
 
     # ------------------------------------------------------------ lifecycle
     def close(self):
@@ -259,6 +260,7 @@ class SlicedNetwork:
             if r is not None:
                 live |= r.any_live
         self.round += 1
+        self._ext_copies.reset()
         self._reduce_round(self.round % 3)
         self._apply_pending(1)
         if not report:
@@ -276,6 +278,7 @@ class SlicedNetwork:
         for s in self.slices:
             s.net.clear(self.epoch)
         self.round = 0
+        self._ext_copies.reset()
 
     def sync(self) -> None:
         self._flush()
@@ -381,11 +384,15 @@ class SlicedNetwork:
                 if r is None:
                     _check(-1)  # no rumor slot for this message
             split.append((r, rpc_encode(pull, b"", 0)))
+        # the bound on recorded copies, which only the owning slice could count
+        add = self._ext_copies.check((node, r, peer) for (node, peer, _), (r, _) in zip(rpcs, split)
+                                     if r is not None)
         mine = []
         for s in self.slices:
             batch = [(node, peer, msg if (r is not None and s.lo <= r < s.hi) else empty)
                      for (node, peer, msg), (r, empty) in zip(rpcs, split)]
             mine.append(s.net.handle_received_batch(batch))
+        self._ext_copies.commit(add)
         per = self._gather_lists(mine)
         return [self._merge([p[i] for p in per]) for i in range(len(rpcs))]
 
