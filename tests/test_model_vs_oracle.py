@@ -7,6 +7,7 @@ import pytest
 import oracle_lib
 from model_bitsliced import Model
 from oracle_lib import SCHED_2P, OracleNet
+from state_edges import STAGGERED, staggered_plan
 
 
 def run(n, R, params=None, seed=0x5AFE6055, epoch=0, kind="origins", max_rounds=40, faults=None,
@@ -18,8 +19,9 @@ def run(n, R, params=None, seed=0x5AFE6055, epoch=0, kind="origins", max_rounds=
     mdl = Model(n, R, seed, epoch, orc.params, L.or_peer, fault_fn, schedule)
     rng = np.random.default_rng(n * 31 + R)
     injected = []
+    plan = staggered_plan(n, R) if kind == "staggered" else {}
     for rnd in range(1, max_rounds + 1):
-        inj = []
+        inj = plan.get(rnd, [])
         if kind == "origins" and rnd == 1:
             inj = [(L.or_origin(seed, epoch, r, n), r) for r in range(R)]
         if kind == "trickle":  # harness: first rumor at a Philox origin, then 50%/node/round
@@ -60,7 +62,7 @@ def run(n, R, params=None, seed=0x5AFE6055, epoch=0, kind="origins", max_rounds=
             got = known[x]
             exp = sum(int(w) << (64 * i) for i, w in enumerate(ok[x]))
             assert got == exp, (rnd, x)
-        if not olive:
+        if not olive and not any(r > rnd for r in plan):
             break
     orc.close()
 
@@ -94,6 +96,14 @@ def test_model_equals_oracle(oracle, n, R, params, kind):
 ])
 def test_model_equals_oracle_faults(oracle, n, R, kind, faults):
     run(n, R, kind=kind, faults=faults)
+
+
+def test_model_equals_oracle_long_lived(oracle):
+    """State rounds and rounds_in_state_b up to 31 (bit 4 of the 5-bit field
+    b, max_rounds 32): the 500 x 16 scenario of tests/state_edges.py, whose
+    coverage tests/test_state_edges_oracle.py asserts."""
+    n, R, params, faults = STAGGERED["500x16"]
+    run(n, R, params, kind="staggered", max_rounds=90, faults=faults)
 
 
 @pytest.mark.parametrize("n,R,kind,params,faults", [
