@@ -211,6 +211,16 @@ const char *gs_round_kernel_name(const gs_engine *e);
  * gather count, so the bytes depend on the state; otherwise
  * gs_round_kernel_bytes (and *launches = 0).  Synchronises. */
 gs_status   gs_round_traffic(gs_engine *e, double *bytes_per_launch, uint32_t *launches);
+/* Which way the deliver+transition launches went since the last gs_clear
+ * (engines of the 2P gather path with 64 <= R_pad <= 512; zeros otherwise):
+ * out[0] launches through the worklist of non-trivial waves (a light pass over
+ * all nodes, then the round kernel over the listed 64-lane waves only), out[1]
+ * launches over the full grid, out[2] | out[3] << 32 the waves listed in all.
+ * SAFE_GOSSIP_AMD_WORKLIST=0 / 1 at gs_create forces the full grid / the
+ * worklist wherever it applies; unset, an epoch starts on the worklist and
+ * goes over to the full grid once about 3/8 of the waves are expected on the
+ * list.  Both ways compute the same.  Synchronises. */
+gs_status   gs_round_path_info(gs_engine *e, uint32_t out[4]);
 
 /* ---- Sharded network (multi-GPU): one engine per rank owns the node range
  * [lo, lo+m), cut into P pipeline parts of mP nodes.  Per round t the caller

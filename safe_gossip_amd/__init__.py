@@ -142,6 +142,7 @@ SYMBOLS = {
     "gs_round_kernel_bytes": (ctypes.c_double, [_P]),
     "gs_round_kernel_name": (ctypes.c_char_p, [_P]),
     "gs_round_traffic": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), _U32P]),
+    "gs_round_path_info": (ctypes.c_int, [_P, _U32P]),
     "gs_peer": (ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                   ctypes.c_uint32, ctypes.c_uint32]),
     "gs_origin": (ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
@@ -796,6 +797,14 @@ class Network:
         b, m = ctypes.c_double(), ctypes.c_uint32()
         _check(self._lib.gs_round_traffic(self._h, ctypes.byref(b), ctypes.byref(m)))
         return float(b.value), int(m.value)
+
+    def round_path_info(self):
+        """(deliver+transition launches through the worklist of non-trivial
+        waves, launches over the full grid, waves listed in all) since the last
+        clear; zeros for engines the worklist does not apply to."""
+        out = (ctypes.c_uint32 * 4)()
+        _check(self._lib.gs_round_path_info(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2]) | (int(out[3]) << 32)
 
 
 class Gossiper:

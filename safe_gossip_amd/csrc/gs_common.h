@@ -188,6 +188,9 @@ struct alignas(16) SibRec {
 // cannot change a result, in bits the records do not otherwise use:
 //   InRec.kf bits 28-30  pusher i = 0..2 pushes nothing (binned tails:
 //                        first < 2^23)
+//   InRec.kf bit 31      some tail pusher (i >= kInline) is live: with bits
+//                        28-30 it tells "no pusher of y is live" without a
+//                        walk of the tail (the worklist pass, round_light)
 //   SibRec.tag bits 5-6  sibling i = 0, 1 is not live or t(x) is complete
 //                        (no creation to pass on); rank < 32
 //   SibRec.e[2] bit 31   the same for sibling 2 (node ids are < 2^29)
@@ -196,6 +199,7 @@ struct alignas(16) SibRec {
 // and a per-source bit map zl = t(x) is live.
 constexpr uint32_t kInSkipShift = 28;
 constexpr uint32_t kInFlagMask = (1u << kInSkipShift) - 1u;
+constexpr uint32_t kInTailLive = 1u << 31;
 constexpr uint32_t kSibSkipShift = 5;
 constexpr uint32_t kSkipBit = 1u << 31;
 constexpr uint32_t kIdMask = kSkipBit - 1u;

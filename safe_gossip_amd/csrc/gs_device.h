@@ -10,7 +10,15 @@ GS_DEV uint32_t popc(u64 v) { return (uint32_t)__popcll(v); }
 
 // Round kernels clear the next in-list build's counters (RoundArgs::zero_*)
 // instead of a memset launch: grid-stride vector stores of buf[0, words), and
-// *one = 0 from the first thread.
+// *one = 0 from the first thread.  (bdim: the block size where the kernel
+// knows it at compile time -- blockDim.x is a load from the dispatch's
+// implicit arguments, and one that a block's first stores make the compiler
+// repeat: a dependent memory round trip each in the block's prologue.)
+GS_DEV void zero_for_build(uint32_t *buf, uint32_t words, u64 *one, uint32_t bdim) {
+    const uint32_t gt = blockIdx.x * bdim + threadIdx.x;
+    for (uint32_t i = gt; i < words; i += gridDim.x * bdim) buf[i] = 0u;
+    if (one && gt == 0u) *one = 0ull;
+}
 GS_DEV void zero_for_build(uint32_t *buf, uint32_t words, u64 *one) {
     const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
     for (uint32_t i = gt; i < words; i += gridDim.x * blockDim.x) buf[i] = 0u;

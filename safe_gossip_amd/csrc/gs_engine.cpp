@@ -68,7 +68,33 @@ struct gs_engine {
     // per 64-bit lane word, otherwise (default) a 32-bit lane word
     uint32_t dlv_pack = 1;
     bool w32 = false;  // 2P gather path: the 32-bit lane round kernel on eligible launches (gs_w32.hip)
-    u64 *acct = nullptr;       // filtered timed launches: class rows counted by the builds (acct[0])
+    u64 *acct = nullptr;       // filtered timed launches: class rows counted by the builds (acct[0]),
+                               // waves listed by the worklist launches among them (acct[1])
+    // Worklist of non-trivial waves (gs_kernels.h RoundArgs::wnz; DESIGN.md
+    // section 4): MODE-1 launches of the single-engine 2P gather path with
+    // one-wave blocks (no faults, no slice, no external RPCs that round) run a
+    // light pass over all nodes and the heavy kernel over the listed waves.
+    // SAFE_GOSSIP_AMD_WORKLIST=0 never, =1 whenever eligible; unset: from each
+    // clear until the listed share of the waves is estimated above
+    // kWlDenseShare.  The estimate is the newest count the device has reported
+    // (wl_host, read without synchronising), grown kWlGrowth-fold per round of
+    // lag -- or, while the host is so far ahead that nothing has been reported,
+    // the injected nodes grown the same way (wl_est).  A wrong estimate costs
+    // time only: both paths compute the same.
+    bool wl_ok = false;
+    int wl_mode = -1;            // 0 / 1 forced, -1 auto
+    bool wl_dense = false;       // auto: dense for the rest of the epoch
+    bool ra_wl = false;          // the round in progress goes through the worklist
+    uint8_t *wnz = nullptr;      // [waves] not all-A
+    uint32_t *wl_list = nullptr, *wl_cnt = nullptr;  // [waves], [2]
+    uint32_t wl_par = 0;         // counter of the next worklist launch (the other one is zero)
+    u64 *wl_total = nullptr;     // waves listed since the last clear
+    u64 *wl_host = nullptr;      // pinned: wl_gen << 32 | count of the last worklist launch
+    uint32_t wl_gen = 0;         // bumped by every clear (counts of an earlier epoch are ignored)
+    double wl_est = 0.0;         // waves expected on the next delivering launch's list, from the injections alone
+    uint32_t wl_grid = 0;        // resident one-wave blocks
+    uint32_t path_wl = 0, path_dense = 0;  // MODE-1 launches by path since the last clear
+    uint32_t acct_wl = 0;        // worklist launches among filt_launches
     uint32_t *pc = nullptr;  // DLV: push codes of the current round [n]
     uint16_t *kn = nullptr;  // single-engine DLV: known masks of the current round [n]
     hipStream_t cstream = nullptr;  // shard engines: plan / in-list side stream
@@ -168,6 +194,14 @@ namespace {
 
 constexpr uint32_t kReduceBlocks = 1024;
 constexpr uint32_t kTimingSlots = 4096;
+// Auto worklist mode: the listed share of the waves above which the engine
+// launches the full grid for the rest of the epoch (half
+// the share, 0.75, at which a forced worklist round first costs more than a
+// full-grid one at config 4), and the growth of the list per round while it is
+// short (measured 3.3-3.5 at configs 3 and 4: a live node pushes to one node
+// and answers the pulls of its pushers), by which a count is brought forward.
+constexpr double kWlDenseShare = 0.375;
+constexpr double kWlGrowth = 3.5;
 
 // A failing HIP call returns GS_ERR_HIP; SAFE_GOSSIP_AMD_DEBUG=1 also names
 // it on stderr (call, line, HIP error).
@@ -228,12 +262,13 @@ void release(gs_engine *e) {
     }
     if (e->ev_main) (void)hipEventDestroy(e->ev_main);
     if (e->cstream) (void)hipStreamDestroy(e->cstream);
-    void *bufs[] = {e->lvm, e->cpm, e->rows_dev, e->acct, e->pc, e->kn, e->Wb, e->sinfo, e->seqw, e->pend, e->offc, e->S[0], e->S[1], e->flags, e->live, e->st32, e->st64, e->inj_key, e->inj_mask, e->obs_known, e->obs_stats,
+    void *bufs[] = {e->wnz, e->wl_list, e->wl_cnt, e->wl_total, e->lvm, e->cpm, e->rows_dev, e->acct, e->pc, e->kn, e->Wb, e->sinfo, e->seqw, e->pend, e->offc, e->S[0], e->S[1], e->flags, e->live, e->st32, e->st64, e->inj_key, e->inj_mask, e->obs_known, e->obs_stats,
                     e->partials, e->obs_state, e->obs_rec, e->obs_psize, e->obs_digest, e->obs_pend, e->ext_dev,
                     e->node_state, e->batch_lists, e->batch_codes};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (e->inj_host) (void)hipHostFree(e->inj_host);
+    if (e->wl_host) (void)hipHostFree(e->wl_host);
     for (hipEvent_t ev : e->tev) (void)hipEventDestroy(ev);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
@@ -256,6 +291,15 @@ gs_status reset_state(gs_engine *e) {
         gs::inlist_cfill_range(e->plan, &first, &words);
         for (auto &c : e->csr)
             if (words && c.scratch) GS_HIP(hipMemsetAsync(c.scratch + first, 0, words * sizeof(uint32_t), e->stream));
+    }
+    if (e->wl_ok) {
+        // (the counter of the next worklist launch is zero already)
+        GS_HIP(hipMemsetAsync(e->wnz, 0, (size_t)gs::wave_count(g), e->stream));
+        GS_HIP(hipMemsetAsync(e->wl_total, 0, sizeof(u64), e->stream));
+        ++e->wl_gen;
+        e->wl_dense = false;
+        e->wl_est = 0.0;
+        e->path_wl = e->path_dense = 0;
     }
     e->cur = 0;
     e->round = 0;
@@ -356,6 +400,12 @@ gs::RoundArgs base_args(gs_engine *e) {
             a.zlm = cs.zl;
             a.lvm = e->lvm;
             a.cpm = e->cpm;
+        }
+        if (e->wl_ok) {
+            a.wnz = e->wnz;
+            a.wl_list = e->wl_list;
+            a.wl_cnt = e->wl_cnt;
+            a.wl_total = e->wl_total;
         }
     }
     a.st32 = e->st32;
@@ -800,6 +850,11 @@ gs_status create_engine(const gs_config *cfg, uint32_t rank, uint32_t world, uin
         const bool off = v && *v == '0';
         e->filt = !off && !e->shard && !e->seq && !e->dlv && e->plan.binned && (g.small || g.W <= 8);
     }
+    {
+        const char *v = std::getenv("SAFE_GOSSIP_AMD_WORKLIST");
+        e->wl_mode = (v && *v) ? (*v != '0' ? 1 : 0) : -1;
+        e->wl_ok = e->filt && !g.small && g.W <= 8 && !e->w32 && !e->slice && !gs::faults_on(e->faults);
+    }
     // Per round a node's Statistics deltas of internal deliveries grow by at
     // most 32*R_pad + 32 (in-degree <= 30 is enforced); fold them into u64
     // well before a wrap.  The delivery-record engines (R_pad <= 16) keep them
@@ -866,7 +921,17 @@ gs_status create_engine(const gs_config *cfg, uint32_t rank, uint32_t world, uin
         ok = dalloc(&e->lvm, gs::node_map_words(n)) == hipSuccess &&
              dalloc(&e->cpm, gs::node_map_words(n)) == hipSuccess &&
              dalloc(&e->rows_dev, 2) == hipSuccess &&
-             dalloc(&e->acct, 1) == hipSuccess && hipMemsetAsync(e->acct, 0, sizeof(u64), e->stream) == hipSuccess;
+             dalloc(&e->acct, 2) == hipSuccess && hipMemsetAsync(e->acct, 0, 2 * sizeof(u64), e->stream) == hipSuccess;
+    if (ok && e->wl_ok) {
+        const size_t waves = (size_t)gs::wave_count(g);
+        ok = dalloc(&e->wnz, waves) == hipSuccess && dalloc(&e->wl_list, waves) == hipSuccess &&
+             dalloc(&e->wl_cnt, 2) == hipSuccess && dalloc(&e->wl_total, 1) == hipSuccess &&
+             hipMemsetAsync(e->wl_cnt, 0, 2 * sizeof(uint32_t), e->stream) == hipSuccess &&
+             hipMemsetAsync(e->wnz, 0, waves, e->stream) == hipSuccess &&
+             hipHostMalloc((void **)&e->wl_host, sizeof(u64), 0) == hipSuccess &&
+             gs::worklist_resident_blocks(e->device, &e->wl_grid) == hipSuccess && e->wl_grid > 0;
+        if (ok) *e->wl_host = 0;
+    }
     if (ok && e->seq)
         ok = dalloc(&e->Wb, (size_t)n * 2 * g.W) == hipSuccess && dalloc(&e->sinfo, n) == hipSuccess &&
              dalloc(&e->seqw, (size_t)gs::seq_blocks(n) * gs::kSeqLists + gs::kSeqLists + n) == hipSuccess;
@@ -1175,6 +1240,35 @@ gs_status round_begin(gs_engine *e) {
         a.rows_cnt = e->rows_dev + (R0 & 1u);  // counted by the build of round t's lists
         e->filt_launches++;
     }
+    // through the worklist?  (auto: until the estimated listed share passes
+    // the one above which the full grid is faster)
+    e->ra_wl = false;
+    const uint32_t wl_tag = (e->wl_gen << 16) | (R0 & 0xFFFFu);
+    if (e->wl_ok) {
+        const double waves = (double)gs::wave_count(e->g);
+        double est = e->wl_est + n_inj;  // (an injected node's wave is listed)
+        e->wl_est = std::min(waves, kWlGrowth * est);
+        if (e->wl_mode < 0 && !e->wl_dense) {
+            const u64 v = __atomic_load_n(e->wl_host, __ATOMIC_RELAXED);
+            const uint32_t tag = (uint32_t)(v >> 32), lag = (R0 - tag) & 0xFFFFu;
+            if ((tag >> 16) == (e->wl_gen & 0xFFFFu) && lag >= 1u && lag < 64u)
+                est = (double)(uint32_t)v * std::pow(kWlGrowth, (double)lag) + n_inj;
+            if (est > kWlDenseShare * waves) e->wl_dense = true;
+        }
+        if (e->wl_mode != 0 && gs::worklist_eligible(a, e->deliver_pending ? 1 : 0))
+            e->ra_wl = e->wl_mode > 0 || !e->wl_dense;
+    }
+    if (e->ra_wl) {
+        a.wl_par = e->wl_par;
+        e->wl_par ^= 1u;
+        a.wl_host = e->wl_host;
+        a.wl_tag = wl_tag;
+        if (a.acct) {
+            a.wl_acct = e->acct + 1;
+            e->acct_wl++;
+        }
+    }
+    if (e->wl_ok && e->deliver_pending) ++(e->ra_wl ? e->path_wl : e->path_dense);
     if (e->shard) {
         GS_HIP(hipStreamWaitEvent(e->stream, e->ev_plan[(R0 + 1) % 3], 0));
         if (e->deliver_pending && !e->dlv) GS_HIP(hipStreamWaitEvent(e->stream, e->ev_edges[R0 % 2], 0));
@@ -1243,7 +1337,8 @@ gs_status launch_part(gs_engine *e, uint32_t h) {
         e->lt1 = t1;
     }
     if (t0) GS_HIP(hipEventRecord(t0, e->stream));
-    GS_HIP(gs::launch_round(a, e->ra_mode, e->stream));
+    if (e->ra_wl) GS_HIP(gs::launch_round_worklist(a, e->wl_grid, e->stream));
+    else GS_HIP(gs::launch_round(a, e->ra_mode, e->stream));
     if (t1) GS_HIP(hipEventRecord(t1, e->stream));
     return GS_OK;
 }
@@ -1585,7 +1680,7 @@ void gs_set_timing(gs_engine *e, int enable) {
     e->tcount = 0;
     if (e->timing && e->filt) {  // restart the traffic accounting with the ring
         (void)hipSetDevice(e->device);
-        if (hipMemsetAsync(e->acct, 0, sizeof(u64), e->stream) == hipSuccess) e->filt_launches = 0;
+        if (hipMemsetAsync(e->acct, 0, 2 * sizeof(u64), e->stream) == hipSuccess) e->filt_launches = e->acct_wl = 0;
     }
 }
 
@@ -2112,6 +2207,10 @@ const char *gs_round_kernel_name(const gs_engine *e) {
     }
     if (e->filt && e->w32 && (e->g.small ? e->g.rpad == 32 : e->g.logr <= 8))
         return "round_kernel_w32<1> (32-bit lanes, live-filtered gathers)";
+    if (e->filt && e->wl_ok && e->wl_mode != 0)
+        return e->wl_mode > 0 ? "round_kernel<false,1> (live-filtered gathers; round_light + worklist of non-trivial waves)"
+                              : "round_kernel<false,1> (live-filtered gathers; round_light + worklist of non-trivial waves "
+                                "while an estimated 3/8 of the waves or fewer)";
     if (e->filt) return e->g.small ? "round_kernel<true,1> (live-filtered gathers)"
                                    : "round_kernel<false,1> (live-filtered gathers)";
     return e->g.small ? "round_kernel<true,1>" : "round_kernel<false,1>";
@@ -2125,6 +2224,13 @@ gs_status gs_round_traffic(gs_engine *e, double *bytes_per_launch, uint32_t *lau
         // plus its zl bit and the two map bits written, and its planes read
         // and written (2 R_pad B); per node class row the build left to gather
         // (pushers, t(x), t(x)'s earlier pushers) 3 planes of R_pad bits.
+        // A launch through the worklist: that per-node term for the nodes of
+        // the listed waves only (64 / W nodes each); the light pass, per node
+        // 48.125 B read (the InRec and SibRec lines of its kf and tag words
+        // 16 + 16, its zl bit, its Statistics deltas 16) and, in an unlisted
+        // wave, the deltas written back (16 B); per wave its byte.  (The rows
+        // term still counts the tail pushers' rows of unlisted nodes, which
+        // such a launch does not gather: an overcount of < 0.1 row per node.)
         gs_status st = set_device(e);
         if (st != GS_OK) return st;
         *launches = e->filt_launches;
@@ -2132,15 +2238,36 @@ gs_status gs_round_traffic(gs_engine *e, double *bytes_per_launch, uint32_t *lau
             *bytes_per_launch = dense;
             return GS_OK;
         }
-        u64 rows = 0;
+        u64 acct[2] = {0, 0};  // rows, waves listed by the worklist launches
         GS_HIP(hipStreamSynchronize(e->stream));
-        GS_HIP(hipMemcpy(&rows, e->acct, sizeof(u64), hipMemcpyDeviceToHost));
-        const double n = e->g.n, rp = e->g.rpad;
-        *bytes_per_launch = n * (68.0 + 3.0 / 8.0 + 2.0 * rp) + 3.0 * rp / 8.0 * (double)rows / e->filt_launches;
+        GS_HIP(hipMemcpy(acct, e->acct, sizeof(acct), hipMemcpyDeviceToHost));
+        const double n = e->g.n, rp = e->g.rpad, per_node = 68.0 + 3.0 / 8.0 + 2.0 * rp;
+        const double waves = (double)gs::wave_count(e->g), wl = e->acct_wl, full = e->filt_launches - e->acct_wl;
+        const double listed_nodes = std::min((double)acct[1] * (64.0 / e->g.W), wl * n);
+        const double total = full * n * per_node + listed_nodes * per_node +
+                             wl * (n * gs::kLightNodeRead + waves) + (wl * n - listed_nodes) * gs::kLightNodeWrite +
+                             3.0 * rp / 8.0 * (double)acct[0];
+        *bytes_per_launch = total / e->filt_launches;
         return GS_OK;
     }
     *bytes_per_launch = dense;
     *launches = 0;
+    return GS_OK;
+}
+
+gs_status gs_round_path_info(gs_engine *e, uint32_t out[4]) {
+    if (!e || !out) return GS_ERR_INVALID_ARGUMENT;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!e->wl_ok) return GS_OK;
+    gs_status st = set_device(e);
+    if (st != GS_OK) return st;
+    u64 listed = 0;
+    GS_HIP(hipStreamSynchronize(e->stream));
+    GS_HIP(hipMemcpy(&listed, e->wl_total, sizeof(u64), hipMemcpyDeviceToHost));
+    out[0] = e->path_wl;
+    out[1] = e->path_dense;
+    out[2] = (uint32_t)listed;
+    out[3] = (uint32_t)(listed >> 32);
     return GS_OK;
 }
 

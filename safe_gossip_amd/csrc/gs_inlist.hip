@@ -134,6 +134,10 @@ GS_DEV uint32_t emit_target(const InListArgs &a, uint32_t y, const uint32_t *lst
 #pragma unroll
     for (uint32_t i = 0; i < kInline; ++i) r.s[i] = i < k ? (lst[i] & kIdMask) : 0u;
     if (filt) r.kf |= (~lv & 7u) << kInSkipShift;  // skip flags of pushers 0..2
+    if (filt) {  // ... and "some tail pusher is live" (1.9 % of nodes have a tail)
+        for (uint32_t i = kInline; i < k; ++i)
+            if (lst[i] & kLiveTag) r.kf |= kInTailLive;
+    }
     a.IN8[y] = r;
     uint32_t rows = filt ? (uint32_t)__popc(lv) + (k > kInline ? k - kInline : 0u) : 0u;
     bool any_live = false;  // some pusher ahead of lst[j] is live

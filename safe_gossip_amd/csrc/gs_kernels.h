@@ -117,6 +117,26 @@ struct RoundArgs {
     // previous round's build consumed)
     uint32_t *zero_buf2;
     uint32_t zero_words2;
+    // Worklist of non-trivial waves (2P gather path, one-wave blocks, live-
+    // filtered).  wnz: a byte per wave (64-lane block of
+    // the transition), 1 = some node of it is not all-A in the planes the last
+    // transition launch wrote; zeroed by gs_clear, and set by the launch in
+    // which the wave leaves all-A (no entry ever returns to A).
+    // launch_round_worklist: round_light lists the waves that have work into
+    // wl_list[0, wl_cnt[wl_par]) and gives the others their Statistics update;
+    // round_kernel<..., WL> then runs the listed waves.  The counters are
+    // double-buffered (the light pass clears wl_cnt[wl_par ^ 1]: no memset
+    // launch).  wl_host (pinned, may be null): wl_tag << 32 | count of the
+    // last worklist launch, for the engine's dense switch (wl_tag: 32 bits
+    // naming the epoch and the round); wl_total += count
+    // (gs_round_path_info), and so does wl_acct (null: launch not timed;
+    // gs_round_traffic).
+    uint8_t *wnz;
+    uint32_t *wl_list, *wl_cnt;
+    uint32_t wl_par;
+    u64 *wl_host;
+    u64 wl_tag;
+    u64 *wl_total, *wl_acct;
     uint32_t dlv_pack;        // DLV transition launches: 0 one node per lane, 1 a 32-bit lane
                               // word of several nodes, 2 a 64-bit one (gs_dlv4.hip)
     Geometry g;
@@ -137,6 +157,19 @@ hipError_t launch_round(const RoundArgs &a, int mode, hipStream_t s);
 // DLV transition launches (modes 0 and 1, no external RPCs) with four nodes
 // per lane (gs_dlv4.hip).
 hipError_t launch_round_dlv4(const RoundArgs &a, int mode, hipStream_t s);
+// A MODE-1 launch of the 2P gather path through the worklist (RoundArgs::wnz):
+// the light pass over all nodes, then the listed waves on `grid` one-wave
+// blocks (a grid-stride loop over the list: any grid >= 1 is correct).  The
+// caller checks worklist_eligible.
+bool worklist_eligible(const RoundArgs &a, int mode);
+hipError_t launch_round_worklist(const RoundArgs &a, uint32_t grid, hipStream_t s);
+// One-wave blocks of the worklist kernel a device holds at once.
+hipError_t worklist_resident_blocks(int device, uint32_t *blocks);
+inline u64 wave_count(const Geometry &g) { return (g.nseg + 63u) / 64u; }
+// Bytes the light pass moves per node (gs_round_traffic): the InRec and SibRec
+// lines its kf / tag words sit in (16 + 16), the zl bit, the Statistics deltas
+// read (16); a node of a trivial wave also has them written (kLightNodeWrite).
+constexpr double kLightNodeRead = 48.125, kLightNodeWrite = 16.0;
 constexpr uint32_t kLiveSlots = 64, kLiveStride = 32;
 // The any-live words of round t+1 (RoundArgs::live) at the end of a
 // transition launch's block.

@@ -52,10 +52,6 @@ static_assert(kRkSmallBlk == 64u || kRkSmallBlk == 128u, "a thread's stage step 
 #ifndef GS_RK_ZSKIP
 #define GS_RK_ZSKIP 1  // one-wave blocks: no plane stores for a wave whose new planes are all A
 #endif
-#ifndef GS_RK_ZSKIP_BLK
-#define GS_RK_ZSKIP_BLK 0  // the same for a whole 256-lane transition block (off: no bench configuration
-                           // runs these blocks, and one SEQ harness mismatch, not reproduced, followed it)
-#endif
 
 #ifndef GS_RK_TAILPRE
 #define GS_RK_TAILPRE 1  // rows of pusher #3 and of t(x)'s sibling #2 issued with the batch (A/B: 0)
@@ -82,12 +78,25 @@ GS_DEV Cls decode16(uint32_t code) {
 // DLV: delivery records (gs_common.h DlvRec) replace every class-plane
 // gather: a lane's pushers' push codes are in its own record and its pull
 // batch in PULL[x], both read coalesced.
-template <bool SMALL, int MODE, bool SHARD, bool SEQ, bool DLV, uint32_t BLK = 256u, bool EXT = false>
-__global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) void round_kernel(RoundArgs a) {
+// WL: the block is one listed wave of a worklist launch (round_kernel below
+// loops over the list); the duties a full grid ties to "every block" or
+// "block 0" (clearing the build's counters, the traffic accounting) are the
+// light pass's then.
+template <bool SMALL, int MODE, bool SHARD, bool SEQ, bool DLV, uint32_t BLK, bool EXT, bool WL>
+GS_DEV void round_block(const RoundArgs &a, const uint32_t wl_bid) {
     constexpr bool DELIVER = (MODE == 1 || MODE == 2);
     static_assert(!EXT || DELIVER, "external RPCs are applied with the round's deliveries");
     constexpr bool TRANSITION = (MODE == 0 || MODE == 1);
+    // (WL: the two early tail rows cost 12 VGPRs across the batch, which the
+    // wave loop does not have at 4 waves per SIMD; their loads go out with
+    // the walks, as in the GS_RK_TAILPRE=0 build)
+    constexpr bool kTailPre = GS_RK_TAILPRE && !WL;
     const Geometry &g = a.g;
+    // the lane's index in the block.  WL: opaque per listed wave, so the lane
+    // constants derived from it are not hoisted out of the wave loop and kept
+    // live across it (141 VGPRs, 3 waves per SIMD, against the full grid's 126)
+    uint32_t tid = threadIdx.x;
+    if constexpr (WL) asm volatile("" : "+v"(tid));
     // words of planes one block owns (its records are contiguous), uint4
     // loads per thread, and the stage (padded node strides: <= 10/8)
     constexpr uint32_t kBlk = BLK;
@@ -96,10 +105,12 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
     constexpr uint32_t kBlockWords = kBlk * kPlanes;
     constexpr uint32_t kStageIters = kBlockWords / 2u / kBlk;
     constexpr uint32_t kStageWords = kBlockWords + kBlockWords / 4u;
-    if (a.zero_buf || a.zero_rows) zero_for_build(a.zero_buf, a.zero_words, a.zero_rows);
-    if (a.zero_buf2) zero_for_build(a.zero_buf2, a.zero_words2, nullptr);
-    const uint32_t bid = (!TRANSITION && a.blk_list) ? a.blk_list[blockIdx.x] : blockIdx.x + a.blk_off;
-    const u64 seg = (u64)bid * blockDim.x + threadIdx.x;
+    static_assert(!WL || (MODE == 1 && BLK == 64u && !SHARD && !EXT), "worklist launches: the 2P gather path's one-wave MODE 1");
+    // (every launch of this kernel has BLK lanes per block: kBlk, not blockDim.x)
+    if (!WL && (a.zero_buf || a.zero_rows)) zero_for_build(a.zero_buf, a.zero_words, a.zero_rows, kBlk);
+    if (!WL && a.zero_buf2) zero_for_build(a.zero_buf2, a.zero_words2, nullptr, kBlk);
+    const uint32_t bid = WL ? wl_bid : (!TRANSITION && a.blk_list) ? a.blk_list[blockIdx.x] : blockIdx.x + a.blk_off;
+    const u64 seg = (u64)bid * kBlk + tid;
     const bool valid = seg < g.nseg;
     Lane<SMALL> L;
     L.init(g, valid ? seg : 0);
@@ -107,9 +118,7 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
     const u64 *__restrict__ S = a.Scur;
 
     __shared__ uint32_t blk_any;  // some node pushes a live rumor in round t+1
-    __shared__ uint32_t blk_nz;   // some node is not all-A in round t+1 (256-lane zero skip)
-    if (threadIdx.x == 0) blk_any = 0;
-    if (threadIdx.x == 0) blk_nz = 0;
+    if (tid == 0) blk_any = 0;
     // the load-issue phase at raised priority: a young wave's requests go out
     // ahead of older waves' compute (issue is by priority, then age)
     __builtin_amdgcn_s_setprio(2);
@@ -131,17 +140,17 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
     };
     // uint4 i = the block's words 2i, 2i + 1 (one node's, 16-B aligned at the
     // padded stride too): the thread's i = tid + kBlk m sit s4 + m s4d apart
-    const uint32_t s4 = sidx(2u * threadIdx.x), s4d = SMALL ? 2u * kBlk : ((kBlk / 4u) >> wlog) * pst;
+    const uint32_t s4 = sidx(2u * tid), s4d = SMALL ? 2u * kBlk : ((kBlk / 4u) >> wlog) * pst;
     const uint32_t npu_blk = SMALL ? (1u << g.lognpu) : 1u;
     const u64 blk_base = (u64)bid * (kBlockWords / npu_blk);
     const uint32_t blk_v4 = (uint32_t)min((u64)(kBlockWords / npu_blk),
                                           g.units * kPlanes * (SMALL ? 1u : g.W) - blk_base) / 2u;
     static_assert(kStageIters == 4, "stage loads are unrolled by hand");
     const uint4 *src4 = reinterpret_cast<const uint4 *>(S + blk_base);
-    const uint4 st0 = src4[min(threadIdx.x, blk_v4 - 1u)];
-    const uint4 st1 = src4[min(threadIdx.x + kBlk, blk_v4 - 1u)];
-    const uint4 st2 = src4[min(threadIdx.x + 2u * kBlk, blk_v4 - 1u)];
-    const uint4 st3 = src4[min(threadIdx.x + 3u * kBlk, blk_v4 - 1u)];
+    const uint4 st0 = src4[min(tid, blk_v4 - 1u)];
+    const uint4 st1 = src4[min(tid + kBlk, blk_v4 - 1u)];
+    const uint4 st2 = src4[min(tid + 2u * kBlk, blk_v4 - 1u)];
+    const uint4 st3 = src4[min(tid + 3u * kBlk, blk_v4 - 1u)];
 
     // ---- coalesced per-node metadata (level 1)
     // Statistics deltas of x, loaded with the other level-1 reads so the
@@ -292,11 +301,11 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
     // ... and that pusher's row, issued as soon as the id is in (the batch's
     // rows, issued after it, stay in flight)
     Cls t0 = {0, 0, 0};
-    if (GS_RK_TAILPRE && DELIVER && !SEQ && !DLV && !SHARD && k > kInline) t0 = L.load_cls(S, tail0);
+    if (kTailPre && DELIVER && !SEQ && !DLV && !SHARD && k > kInline) t0 = L.load_cls(S, tail0);
     // likewise the row of t(x)'s pusher #kBatchE ahead of x (its id is inline)
     static_assert(kBatchE < kSibInline, "sibling #kBatchE is inline");
     Cls s2 = {0, 0, 0};
-    if (GS_RK_TAILPRE && DELIVER && !SEQ && !DLV && !SHARD && r > kBatchE && !(tgw & kTgNoPull) &&
+    if (kTailPre && DELIVER && !SEQ && !DLV && !SHARD && r > kBatchE && !(tgw & kTgNoPull) &&
         (!filt || zneed) && !((eskip >> kBatchE) & 1u))
         s2 = L.load_cls(S, pick_sib(sb8.e, kBatchE));
     __builtin_amdgcn_s_setprio(0);
@@ -326,6 +335,8 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
     const u64 C = isC & ~(a0 & a1);
     const u64 D = isC & a0 & a1;
     const u64 liveX = B | C;
+    // the wave is all-A in round t (one-wave transition blocks: RoundArgs::wnz below)
+    const bool wave_was_a = kBlk == 64u && TRANSITION && !SHARD && __ballot(valid && (isC | a0 | a1) != 0ull) == 0ull;
 
     // ---- phases 1 and 2 of round t at x (Gossip::receive)
     // Faults: a node offline in round t (off_t) has no pushers and no pull; its
@@ -476,7 +487,7 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
                 const uint32_t s = i < kInline ? pick_inline(in8.s, i)
                                                : (i == kInline ? tail0 : a.src[in8.first() + (i - kInline)]);
                 zin |= s == z;
-                rv.push((GS_RK_TAILPRE && i == kInline) ? t0 : L.load_cls(S, s), i, k, !(pulled && s == z));
+                rv.push((kTailPre && i == kInline) ? t0 : L.load_cls(S, s), i, k, !(pulled && s == z));
             }
             // Pull batch from z: z's live set plus what z created from pushers
             // ahead of x.
@@ -496,7 +507,7 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
                 for (uint32_t i = kBatchE; i < min(r, kSibInline); ++i) {
                     const bool sk = ((eskip >> i) & 1u) != 0;
                     Cls row;
-                    if (GS_RK_TAILPRE && i == kBatchE) {
+                    if (kTailPre && i == kBatchE) {
                         row = s2;
                     } else {
                         row = sib_row(pick_sib(sb8.e, i), sk);
@@ -772,7 +783,7 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
         }
         const u64 bl = __ballot(valid && lvw != 0);
         const u64 bc = __ballot(valid && aw == 0);
-        const uint32_t lane = threadIdx.x & 63u;
+        const uint32_t lane = tid & 63u;
         const u64 seg0 = seg - lane;
         if (lane == 0 && seg0 < g.nseg) {
             if (SMALL) {  // a lane per node: the wave's 64 nodes are one map word
@@ -801,26 +812,25 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
         }
         // traffic accounting of timed launches: the class rows this round's
         // build left to gather (counted there, off the kernel's path)
-        if (MODE == 1 && a.acct && a.rows_cnt && bid == 0 && threadIdx.x == 0) atomicAdd(a.acct, *a.rows_cnt);
+        if (MODE == 1 && !WL && a.acct && a.rows_cnt && bid == 0 && tid == 0) atomicAdd(a.acct, *a.rows_cnt);
     }
 
     // ---- write round-(t+1) planes (through LDS, 16-byte coalesced stores)
     uint32_t live_new = (valid && on_next) ? popc(Bn | Cn) : 0u;
     if (!SMALL) live_new = group_sum(live_new, g.W);
-    if (__ballot(live_new != 0u) != 0ull && (threadIdx.x & 63u) == 0u) blk_any = 1u;
-    constexpr bool kZBlk = GS_RK_ZSKIP_BLK && TRANSITION && kBlk != 64u;
-    const u64 nz_mask = SMALL ? L.m : ~0ull;
-    if (kZBlk && __ballot(valid && ((N[0] | N[1] | N[2]) & nz_mask) != 0ull) != 0ull && (threadIdx.x & 63u) == 0u)
-        blk_nz = 1u;
+    if (__ballot(live_new != 0u) != 0ull && (tid & 63u) == 0u) blk_any = 1u;
     __syncthreads();  // also: every lane is done reading stage
     const bool blk_live = blk_any != 0u;
     __builtin_amdgcn_s_setprio(1);  // the drain: retire the block, free its slot
     // A wave (= block) whose nodes are all-A in round t+1 were all-A in
     // round t-1 as well (no entry ever returns to A; clear zeroes both
     // buffers), and Snext holds round t-1: its zero planes are there already.
-    // (a 256-lane block: the same over its four waves, from blk_nz)
-    const bool zskip = kZBlk ? blk_nz == 0u
-                             : GS_RK_ZSKIP && kBlk == 64u && __ballot(valid && (N[0] | N[1] | N[2]) != 0ull) == 0ull;
+    const bool wave_nz = kBlk == 64u && __ballot(valid && (N[0] | N[1] | N[2]) != 0ull) != 0ull;
+    const bool zskip = GS_RK_ZSKIP && kBlk == 64u && !wave_nz;
+    // ... and the same ballot as a byte per wave, which the next launch's
+    // worklist pass reads (RoundArgs::wnz): stored once per epoch and wave,
+    // by the launch in which the wave leaves all-A
+    if (kBlk == 64u && !SHARD && a.wnz && wave_nz && wave_was_a && tid == 0) a.wnz[bid] = 1u;
     if (zskip) {
         // nothing to store
     } else if (SMALL) {
@@ -840,7 +850,7 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
         uint4 *dst4 = reinterpret_cast<uint4 *>(a.Snext + blk_base);
         // streaming (nontemporal) stores: 3.11 -> 3.01 ms per round kernel at
         // config 4 (nontemporal plane loads measured slower: 3.27 ms).
-        for (uint32_t i = threadIdx.x, si = s4; i < blk_v4; i += blockDim.x, si += s4d)
+        for (uint32_t i = tid, si = s4; i < blk_v4; i += kBlk, si += s4d)
             nt_store4(*reinterpret_cast<const uint4 *>(&stage[si]), &dst4[i]);
     }
     if (SHARD) {
@@ -890,6 +900,45 @@ __global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) v
         v.w += d_recv;                             // full_message_received
         store_stats(a.st32, a.st16, x, v);
         if (!on_next) atomicAdd(&a.offc[x], 1u);  // (no return: nothing waits for it)
+    }
+}
+
+template <bool SMALL, int MODE, bool SHARD, bool SEQ, bool DLV, uint32_t BLK = 256u, bool EXT = false, bool WL = false>
+__global__ __launch_bounds__(BLK, BLK == 256u ? GS_RK_MINW : GS_RK_MINW_SMALL) void round_kernel(RoundArgs a) {
+    if constexpr (WL) {
+        // the listed waves, in list order (each wave is independent: the
+        // planes are double-buffered, Statistics per node)
+        // (readfirstlane: the count and the wave ids are loaded from memory
+        // this launch's stream also writes, so not with scalar loads; they are
+        // uniform, and everything derived from bid stays in SGPRs as in the
+        // full-grid kernel)
+        const uint32_t cnt = __builtin_amdgcn_readfirstlane(a.wl_cnt[a.wl_par]);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {  // for the engine: the dense switch, the observers
+            if (a.wl_host) __hip_atomic_store(a.wl_host, (a.wl_tag << 32) | cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            atomicAdd(a.wl_total, (u64)cnt);
+            if (a.wl_acct) atomicAdd(a.wl_acct, (u64)cnt);
+        }
+        const uint32_t *list = a.wl_list;
+        for (uint32_t i = blockIdx.x; i < cnt; i += gridDim.x) {
+            // The arguments are read again from the kernel-argument segment
+            // (RoundArgs is the kernel's only argument: offset 0) for every
+            // listed wave, through a pointer the compiler cannot see through:
+            // loop-invariant argument words would otherwise stay live in SGPRs
+            // across the whole body (116 spilled into VGPR lanes, and their
+            // VGPR copies hoisted: 141 VGPRs against the full grid's 126).
+#if defined(__HIP_DEVICE_COMPILE__)
+            const __attribute__((address_space(4))) RoundArgs *pa =
+                (const __attribute__((address_space(4))) RoundArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(pa));
+            const RoundArgs b = *pa;
+#else
+            const RoundArgs &b = a;  // (the host pass only parses the kernel)
+#endif
+            round_block<SMALL, MODE, SHARD, SEQ, DLV, BLK, EXT, true>(b, __builtin_amdgcn_readfirstlane(list[i]));
+            __syncthreads();  // the stage and blk_any are the next wave's
+        }
+    } else {
+        round_block<SMALL, MODE, SHARD, SEQ, DLV, BLK, EXT, false>(a, 0u);
     }
 }
 
@@ -956,6 +1005,141 @@ hipError_t launch_round(const RoundArgs &a, int mode, hipStream_t s) {
     }
     if (w32_eligible(a, mode)) return launch_round_w32(a, mode, s);                   // gs_w32.hip
     return a.g.small ? launch_mode<true, false, false>(a, mode, s) : launch_mode<false, false, false>(a, mode, s);
+}
+
+// ------------------------------------------------------------ worklist
+// The light pass of a worklist launch (MODE 1, the 2P gather path's one-wave
+// blocks; RoundArgs::wnz).  A node x is TRIVIAL in the launch that delivers
+// round t and transitions to t+1 when
+//   * its wave's byte is 0: x is all-A in round t (and so was in t-1: its
+//     zero planes are in Snext already, the premise of GS_RK_ZSKIP),
+//   * no pusher of x is live (InRec.kf: the skip flags of pushers 0..2 and the
+//     tail flag),
+//   * its pull is empty: t(x) is not live (zl) and no live sibling ahead of x
+//     could have created anything at t(x) (no SibRec of this build; the
+//     filtered build writes one only with kSibZNeed),
+//   * no rumor is injected at x for round t+1.
+// Such a node stays all-A, its map bits stay 0 / 0, it is not live, and its
+// Statistics move by empty_pull_sent += k (its k pushers each get an empty
+// pull row) and empty_push_sent += 1 (round_block: d_empty_pull, d_empty_push
+// with lc = 0, first_create = none, live_new = 0; src/gossip.rs:79-113,
+// 139-147).  A wave whose nodes are all trivial gets exactly that here, from
+// coalesced independent loads with no LDS stage; every other wave is appended
+// to the list for round_kernel<..., WL> and left alone.  One returning atomic
+// per block that lists something (2048 nodes: at 2^24 nodes at most 8192 of
+// them, ~0.1 ms of same-word atomics spread over the pass).
+constexpr uint32_t kLightThreads = 512u, kLightPer = 4u, kLightNodes = kLightThreads * kLightPer;
+__global__ __launch_bounds__(kLightThreads) void round_light(RoundArgs a) {
+    const Geometry &g = a.g;
+    __shared__ uint32_t s_cnt, s_base;
+    if (threadIdx.x == 0) s_cnt = 0u;
+    // what a full-grid round kernel ties to "every block" and to "block 0"
+    if (a.zero_buf || a.zero_rows) zero_for_build(a.zero_buf, a.zero_words, a.zero_rows, kLightThreads);
+    if (a.zero_buf2) zero_for_build(a.zero_buf2, a.zero_words2, nullptr, kLightThreads);
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < kLiveSlots)  // round t's any-live words (mark_any_live)
+            __hip_atomic_store(&a.live[(((a.round_new + 1u) & 1u) * kLiveSlots + threadIdx.x) * kLiveStride], 0u,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x == 0) {
+            a.wl_cnt[a.wl_par ^ 1u] = 0u;  // the next worklist launch's counter
+            if (a.acct && a.rows_cnt) atomicAdd(a.acct, *a.rows_cnt);
+        }
+    }
+    __syncthreads();
+    const uint32_t lw = g.logr - 6u, glog = 6u - lw;  // W = 2^lw lanes per node, 2^glog nodes per wave
+    const uint32_t lane = threadIdx.x & 63u, gfirst = lane & ~((1u << glog) - 1u);
+    const u64 gbits = (glog == 6u ? ~0ull : ((1ull << (1u << glog)) - 1ull)) << gfirst;
+    const u64 below = (1ull << lane) - 1ull;
+    const uint32_t x0 = blockIdx.x * kLightNodes + threadIdx.x;
+    const uint32_t serial = a.serial & kSerialMask;
+    uint32_t kf[kLightPer], tag[kLightPer], zw[kLightPer], wb[kLightPer];
+    uint4 sv[kLightPer];
+#pragma unroll
+    for (uint32_t i = 0; i < kLightPer; ++i) {
+        const uint32_t x = x0 + i * kLightThreads, xi = x < g.n ? x : 0u;
+        kf[i] = a.IN8[xi].kf;
+        tag[i] = a.SIB8[xi].tag;
+        zw[i] = reinterpret_cast<const uint32_t *>(a.zlm)[xi >> 5];
+        wb[i] = a.wnz[xi >> glog];
+        sv[i] = load_stats(a.st32, a.st16, xi);
+    }
+    uint32_t off[kLightPer], rank[kLightPer];
+    bool lead[kLightPer];
+#pragma unroll
+    for (uint32_t i = 0; i < kLightPer; ++i) {
+        const uint32_t x = x0 + i * kLightThreads;
+        const bool ok = x < g.n;
+        bool work = wb[i] != 0u || ((kf[i] >> kInSkipShift) & 7u) != 7u || (kf[i] & kInTailLive) != 0u ||
+                    (tag[i] >> 8) == serial || ((zw[i] >> (x & 31u)) & 1u) != 0u;
+        if (a.n_inj && ok) {  // as find_injection, over the node's W segment keys
+            const u64 k0 = (u64)x << lw, k1 = ((u64)x + 1u) << lw;
+            uint32_t lo = 0, hi = a.n_inj;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (a.inj_key[mid] < k0) lo = mid + 1; else hi = mid;
+            }
+            work |= lo < a.n_inj && a.inj_key[lo] < k1;
+        }
+        const bool wave_work = (__ballot(ok && work) & gbits) != 0ull;  // the vote of x's wave
+        if (ok && !wave_work) {
+            uint4 v = sv[i];
+            v.x += kf[i] & ((1u << kFirstShift) - 1u);  // empty_pull_sent += k
+            v.y += 1u;                                  // empty_push_sent
+            store_stats(a.st32, a.st16, x, v);
+        }
+        lead[i] = ok && wave_work && lane == gfirst;  // (a wave's first node is its lowest: valid if any is)
+        const u64 lb = __ballot(lead[i]);
+        rank[i] = popc(lb & below);
+        uint32_t o = 0u;
+        if (lane == 0u && lb) o = atomicAdd(&s_cnt, popc(lb));
+        off[i] = __shfl(o, 0, 64);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) s_base = s_cnt ? atomicAdd(&a.wl_cnt[a.wl_par], s_cnt) : 0u;
+    __syncthreads();
+    const uint32_t base = s_base;
+#pragma unroll
+    for (uint32_t i = 0; i < kLightPer; ++i)
+        if (lead[i]) a.wl_list[base + off[i] + rank[i]] = (x0 + i * kLightThreads) >> glog;
+}
+
+bool worklist_eligible(const RoundArgs &a, int mode) {
+    return GS_RK_ZSKIP && kRkSmallBlk == 64u && mode == 1 && !a.g.small && a.g.W <= 8u && !a.recvA && !a.Wb &&
+           !a.DR && a.zlm && a.lvm && a.cpm && a.wnz && a.wl_list && a.wl_cnt && a.wl_total && a.n_ext == 0 && !faults_on(a.f) &&
+           !a.emin && !a.eadd && !a.st16 && a.blk_off == 0 && a.blk_count == 0 && !a.blk_list &&
+           !w32_eligible(a, mode);
+}
+
+hipError_t launch_round_worklist(const RoundArgs &a, uint32_t grid, hipStream_t s) {
+    if constexpr (kRkSmallBlk == 64u) {
+        if (!worklist_eligible(a, 1) || grid == 0) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(round_light, dim3((a.g.n + kLightNodes - 1u) / kLightNodes), dim3(kLightThreads), 0, s, a);
+        hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+        RoundArgs h = a;  // (done by the light pass)
+        h.zero_buf = h.zero_buf2 = nullptr;
+        h.zero_rows = nullptr;
+        h.acct = nullptr;
+        const uint32_t blocks = (uint32_t)std::min<u64>(grid, wave_count(a.g));
+        hipLaunchKernelGGL((round_kernel<false, 1, false, false, false, 64u, false, true>), dim3(blocks), dim3(64), 0, s, h);
+        return hipGetLastError();
+    } else {
+        return hipErrorInvalidValue;
+    }
+}
+
+hipError_t worklist_resident_blocks(int device, uint32_t *blocks) {
+    *blocks = 0;
+    if constexpr (kRkSmallBlk == 64u) {
+        int per_cu = 0, cus = 0;
+        hipError_t err = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per_cu, round_kernel<false, 1, false, false, false, 64u, false, true>, 64, 0);
+        if (err != hipSuccess) return err;
+        err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+        if (err != hipSuccess) return err;
+        *blocks = (uint32_t)std::max(per_cu, 1) * (uint32_t)std::max(cus, 1);
+    }
+    return hipSuccess;
 }
 
 // Rumor slices: add a round's empty-RPC counts, reduced with MIN over the
